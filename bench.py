@@ -21,6 +21,13 @@ bracketed by barrier + synchronize on every rank, MAX elapsed over ranks.
 TTFT p50 is over every request of the timed steps.  tokens/s counts the whole
 reply (prefill time included), so it is the user-visible rate.
 
+A run does only that: set-up (weights, GEMM autotune, decode graph), warm-up,
+the timed steps, the JSON line.  Prompts and weights are seeded, so two runs
+with the same arguments see identical inputs; ``--dump-outputs DIR`` writes the
+token ids the last timed step returned (``DIR/tokens.npy``) so that two builds
+can be compared.  Secondary measurements live in ``bench/*.py``, none here:
+``--full`` is accepted and adds nothing.
+
 Launch: ``python bench.py`` (1 GPU), ``python bench.py --gpus N`` (spawns the N
 rank processes itself, before any GPU call), or under
 ``python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1
@@ -68,6 +75,13 @@ def parse(argv=None):
                     help="cpu: gloo + the CPU engine (plumbing tests with tiny models)")
     ap.add_argument("--layers", type=int, default=None,
                     help="override n_layers (tests only; a reduced model is not a valid bench)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned to its caller "
+                         "as DIR/tokens.npy: the generated token ids, float64 [replicas * peers, "
+                         "new_tokens], replicas in rank order")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary measurement; this benchmark has none (a run "
+                         "measures its headline figure only), so the option changes nothing")
     return ap.parse_args(argv)
 
 
@@ -201,6 +215,20 @@ def run(a):
         dist.all_gather_object(gathered, ttfts)
         all_ttft = [x for g in gathered for x in g]
     elapsed, total_toks = float(t[0]), float(t[1])
+    if a.dump_outputs:
+        if a.steps < 1:
+            raise SystemExit("bench: --dump-outputs needs at least one timed step")
+        # EOS is ignored, so every reply has new_tokens ids; a TP/EP group reports once
+        rows = [r.tokens for r in res] if sub_rank == 0 else []
+        if world > 1:
+            gathered = [None] * world
+            dist.all_gather_object(gathered, rows)
+            rows = [x for g in gathered for x in g]
+        if rank == 0:
+            import numpy as np
+
+            os.makedirs(a.dump_outputs, exist_ok=True)
+            np.save(os.path.join(a.dump_outputs, "tokens.npy"), np.asarray(rows, dtype=np.float64))
     graphs = list(getattr(eng, "_graphs", {}).values())
     captured = bool(graphs) and all(g.graph is not None for g in graphs)
     if rank == 0:

@@ -45,6 +45,24 @@ def test_bench_spawns_ranks(n, extra, par):
         assert k in out
 
 
+def test_bench_dumps_last_step_outputs(tmp_path):
+    """``--dump-outputs DIR``: the last timed step's token ids, one float64 row per peer of
+    every replica, identical between two runs with the same arguments; ``--full`` is accepted."""
+    import numpy as np
+
+    args = ["--gpus", "2", "--model", "tiny-llama", "--peers", "2"]
+    outs = []
+    for d, extra in (("a", []), ("b", ["--full"])):
+        res = _bench(*args, *extra, "--dump-outputs", str(tmp_path / d))
+        assert os.listdir(tmp_path / d) == ["tokens.npy"]
+        outs.append(np.load(tmp_path / d / "tokens.npy"))
+        assert res["steps"] == 1 and res["ms_per_step"] > 0
+    assert outs[0].dtype == np.float64 and outs[0].shape == (4, 4)  # 2 replicas x 2 peers, 4 tokens
+    assert (outs[0] == outs[0].round()).all() and (outs[0] >= 0).all()
+    assert (outs[0] == outs[1]).all()
+    assert not (outs[0][0] == outs[0][2]).all()  # replicas differ (seed, message): both gathered
+
+
 def test_bench_rejects_world_mismatch():
     e = dict(os.environ, WORLD_SIZE="1", RANK="0", LOCAL_RANK="0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--device", "cpu",
