@@ -95,7 +95,12 @@ EXPERIMENTAL_LIB = os.path.join(LIBDIR, "libp2p_experimental.so")
 # Kernels whose k loop streams through inline-asm loads (csrc/kernels/wide_gemm.hip): the
 # compiler does not know those registers are still in flight, so a spill of one would read
 # it before it lands.  Their translation units must compile with zero scratch.
-NO_SCRATCH = {"wide_gemm.hip", "tiled_gemm.hip"}
+NO_SCRATCH = {"wide_gemm.hip", "tiled_gemm.hip", "mx4_gemm.hip"}
+# (mx4_gemm.hip: plain loads, but its launch ladder promises instantiations that fit the
+# register file -- a spilling one means the ladder's estimate is off)
+
+# Per-unit extra flags.  mx4_gemm.hip: no packed-fp32 VALU ops (v_pk_*_f32) in its code
+UNIT_FLAGS = {"mx4_gemm.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def check_no_scratch(src, remarks: str, obj=None):
@@ -141,9 +146,10 @@ def build_kernels(force=False, jobs=8, experimental=False):
         if force or _stale(o, [s] + hdrs):
             todo.append((s, o))
     def compile_one(s, o):
+        uflags = flags + UNIT_FLAGS.get(os.path.basename(s), [])
         if os.path.basename(s) not in NO_SCRATCH:
-            return _run([HIPCC] + flags + ["-c", s, "-o", o])
-        out = _run([HIPCC] + flags + ["-Rpass-analysis=kernel-resource-usage", "-c", s, "-o", o])
+            return _run([HIPCC] + uflags + ["-c", s, "-o", o])
+        out = _run([HIPCC] + uflags + ["-Rpass-analysis=kernel-resource-usage", "-c", s, "-o", o])
         check_no_scratch(s, out, o)
         return out
 

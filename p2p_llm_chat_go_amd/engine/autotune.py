@@ -89,8 +89,8 @@ def pick(times: dict, order: list) -> int:
     return min(times, key=times.get)
 
 
-def _job_key(name, N, K, M, fp8) -> str:
-    return "%s:N%d:K%d:M%d%s" % (name, N, K, M, ":fp8" if fp8 else "")
+def _job_key(name, N, K, M, fmt) -> str:
+    return "%s:N%d:K%d:M%d%s" % (name, N, K, M, "" if fmt == "bf16" else ":" + fmt)
 
 
 def _configs(K, M=1, tiled=False, midm=False, wide=False):
@@ -178,9 +178,15 @@ def autotune_model(model, batch_sizes=(1,), verbose=False, table: dict | None = 
         for name, wts, epi, fn in jobs:
             N, K = G.tiled_shape(wts[0])
             times = {}
-            bf = not G._is_f8(wts[0])
-            codes = _configs(K, M, G.tiled_ok(N, K, epi) and bf, midm=bf,
-                             wide=bf and G.wide_ok(N, K, epi))
+            fmt = G._fmt(wts[0])
+            bf = fmt == "bf16"
+            norm = epi in (G.EPI_QKV_ROPE, G.EPI_SILU, G.EPI_ARGMAX)
+            if fmt == "mx4":  # the MXFP4 kernel's own ladder (waves x U x NG), nothing else
+                codes = [c for c in G.MX4_CODES if G.mx4_code_ok(M, K, N, epi, norm, c)
+                         and (K // 128) // (c & 0xff) >= 1]
+            else:
+                codes = _configs(K, M, G.tiled_ok(N, K, epi) and bf, midm=bf,
+                                 wide=bf and G.wide_ok(N, K, epi))
             if bf and epi == G.EPI_ARGMAX and M == 1 and G.wide_ok(N, K, epi):
                 # the 1 GB LM head stream: the wide kernel's 8 x 3 chunks of weights in flight
                 # per workgroup against the skinny launches
@@ -191,7 +197,7 @@ def autotune_model(model, batch_sizes=(1,), verbose=False, table: dict | None = 
                 # pack the activations fragment-major first (one extra launch, timed with the
                 # GEMM): measured to pay on the qkv shape only (profiles/r3_afrag_probe.jsonl)
                 codes += [c | G.AFRAG_FLAG for c in _configs(K, M) if (c >> 16) & 0xff]
-            jk = _job_key(name, N, K, M, not bf)
+            jk = _job_key(name, N, K, M, fmt)
             fixed = table.get(jk)
             if fixed is not None and int(fixed) in codes:
                 times[int(fixed)] = _graph_time(lambda: [fn(wt, int(fixed)) for wt in wts])
@@ -202,7 +208,6 @@ def autotune_model(model, batch_sizes=(1,), verbose=False, table: dict | None = 
                 best = pick(times, codes)
             if record is not None:
                 record[jk] = best
-            norm = epi in (G.EPI_QKV_ROPE, G.EPI_SILU, G.EPI_ARGMAX)
             G.set_tune(G.tune_key(wts[0], M, epi, norm), best)
             if epi == G.EPI_RESID:
                 # TP row-parallel projections run the same shape with other epilogues

@@ -68,20 +68,25 @@ class Engine:
         self.cfg = cfg
         self.device = torch.device(device)
         own = weights is None
+        # weight_dtype "fp8": weight-only e4m3 dense projections (EngineWeights.quantize_fp8);
+        # "mxfp4": weight-only OCP MXFP4 projections + FP8 LM head (EngineWeights.quantize_mxfp4)
+        self.weight_dtype = weight_dtype or os.environ.get("ENGINE_WEIGHTS", "bf16")
+        if self.weight_dtype == "mxfp4" and max(tp_size, 1 if own else weights.tp_size) > 1:
+            raise ValueError("weight_dtype mxfp4 runs on one GPU only (tp_size 1): the fused "
+                             "all-reduce epilogue has no MXFP4 kernel")
         if own:
             weights = EngineWeights.random(cfg, self.device, seed=seed, tp_rank=tp_rank,
                                            tp_size=tp_size, ep_rank=ep_rank, ep_size=ep_size)
-        # weight_dtype "fp8": weight-only e4m3 dense projections (EngineWeights.quantize_fp8)
-        self.weight_dtype = weight_dtype or os.environ.get("ENGINE_WEIGHTS", "bf16")
-        if self.weight_dtype == "fp8":
+        if self.weight_dtype in ("fp8", "mxfp4"):
             # a caller's store stays bf16 (it may back a reference engine); ours is swapped
-            weights = (weights if own else weights.shallow_copy()).quantize_fp8()
+            weights = weights if own else weights.shallow_copy()
+            weights = weights.quantize_fp8() if self.weight_dtype == "fp8" else weights.quantize_mxfp4()
             if self.device.type == "cuda":
                 # the bf16 originals and the quantizer's fp32 temporaries stay reserved in
                 # torch's caching allocator; release them before sizing the KV pool
                 torch.cuda.empty_cache()
         elif self.weight_dtype != "bf16":
-            raise ValueError("weight_dtype must be bf16 or fp8, got %r" % self.weight_dtype)
+            raise ValueError("weight_dtype must be bf16, fp8 or mxfp4, got %r" % self.weight_dtype)
         self.weights = weights
         if kv_pages is None:
             self.kv = KVCache.from_free_memory(cfg, self.device, fraction=kv_fraction,

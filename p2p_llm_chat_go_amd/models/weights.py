@@ -62,6 +62,8 @@ class EngineWeights:
         def nb(t):
             if isinstance(t, ops.Fp8Weight):
                 return t.data.numel() + 4 * t.scale.numel()
+            if isinstance(t, ops.Mx4Weight):
+                return t.nbytes()
             return t.numel() * t.element_size()
 
         n = nb(self.embed) + nb(self.lm_head)
@@ -92,6 +94,18 @@ class EngineWeights:
                 ops.tiled_shape(self.lm_head)[1] % 64 == 0:
             self.lm_head = ops.quantize_fp8(self.lm_head)
         return self
+
+    def quantize_mxfp4(self, names=("qkv", "o", "gate_up", "down")) -> "EngineWeights":
+        """Weight-only MXFP4 (OCP e2m1 codes, one e8m0 scale per 32 elements along K: 4.25
+        bits per weight) for the dense projections, in place; the LM head goes to the FP8
+        path (a 4-bit LM head costs quality for 3 % of the bytes).  The embedding, router and
+        MoE experts stay bf16.  Opt-in (ENGINE_WEIGHTS=mxfp4)."""
+        for lw in self.layers:
+            for name in names:
+                t = getattr(lw, name)
+                if isinstance(t, torch.Tensor):
+                    setattr(lw, name, ops.quantize_mxfp4(t))
+        return self.quantize_fp8(names=(), lm_head=True)
 
     # ------------------------------------------------------------------ build
     @classmethod

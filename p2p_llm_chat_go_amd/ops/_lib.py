@@ -92,6 +92,13 @@ _SIGS = {
     "p2p_skinny_gemm_qkv_rope": [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p,
                                  c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_float,
                                  c_int, c_void_p, c_void_p],
+    # MXFP4 weight-only skinny GEMM (mx4_gemm.hip): codes, scales, then as the skinny pair
+    "p2p_mx4_gemm": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
+                     c_void_p, c_int, c_float, c_int, c_void_p],
+    "p2p_mx4_gemm_qkv_rope": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                              c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                              c_float, c_int, c_void_p],
+    "p2p_mx4_gemm_ok": [c_int, c_int, c_int, c_int, c_int, c_int],
     "p2p_sample": [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                    c_void_p, c_void_p],
     "p2p_topk_candidates": [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p],

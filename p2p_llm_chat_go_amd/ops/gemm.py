@@ -23,7 +23,7 @@ EPI_QKV_ROPE, EPI_ARGMAX = 4, 5
 EPI_AR = 6  # TP row-parallel projection + fused all-reduce + residual (skinny_gemm_ar)
 SKINNY_MAX_M = 64
 
-# Autotuned launch codes: (N, K, epi, norm, m_tile[, "fp8"]) -> waves | (U << 8)
+# Autotuned launch codes: (N, K, epi, norm, m_tile[, "fp8" | "mx4"]) -> waves | (U << 8)
 # (engine/autotune.py)
 _TUNE: dict = {}
 
@@ -91,12 +91,114 @@ def unpair_f8(t: torch.Tensor) -> torch.Tensor:
     return t.reshape(G, S // 2, 64, 2, 8).transpose(2, 3).contiguous().reshape(G, S, 64, 8)
 
 
+E2M1 = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)  # OCP fp4 magnitudes by code (bit 3 = sign)
+
+
+class Mx4Weight:
+    """Weight-only MXFP4 projection (OCP MX v1.0: e2m1 codes, one e8m0 scale per 32 elements
+    along K), in the two planes ``csrc/kernels/mx4_gemm.hip`` streams:
+
+    ``data``  uint8 ``[N/16, K/128, 64, 16]``: fragment order with four consecutive k-steps
+              interleaved per lane -- lane l's 16 bytes at super-step p are four 32-bit words,
+              word h = its 8 codes of k-step 4p + h (nibble j = element j, low nibble first);
+    ``scale`` uint8 ``[N/16, K/128, 16, 4]``: word (g, p, r) = the scale bytes of column
+              16g + r for k-steps 4p .. 4p + 3.
+
+    ``shape`` is the fragment-major shape of the bf16 weight it stands for (``tiled_shape``
+    and the engine's shape arithmetic work unchanged).  Not a ``torch.Tensor``."""
+
+    def __init__(self, data: torch.Tensor, scale: torch.Tensor):
+        self.data = data
+        self.scale = scale
+
+    @property
+    def shape(self):
+        G, P = self.data.shape[0], self.data.shape[1]
+        return torch.Size((G, 4 * P, 64, 8))
+
+    @property
+    def device(self):
+        return self.data.device
+
+    def numel(self):
+        return 2 * self.data.numel()
+
+    def to(self, device):
+        return Mx4Weight(self.data.to(device), self.scale.to(device))
+
+    def element_size(self):
+        return 0.5
+
+    def nbytes(self) -> int:
+        return self.data.numel() + self.scale.numel()
+
+    def dequantize_f32(self) -> torch.Tensor:
+        """Exact fp32 [N, K] (natural layout) values the kernel multiplies with."""
+        G, P = self.data.shape[0], self.data.shape[1]
+        dev = self.data.device
+        d = self.data.reshape(G, P, 64, 4, 4).permute(0, 1, 3, 2, 4).reshape(G, 4 * P, 64, 4)
+        codes = untile_weight(torch.stack([d & 15, d >> 4], -1).reshape(G, 4 * P, 64, 8)).long()
+        mag = torch.tensor(E2M1, device=dev)[codes & 7]
+        val = torch.where(codes >= 8, -mag, mag)
+        e = self.scale.permute(0, 2, 1, 3).reshape(G * 16, 4 * P).int() - 127
+        s = torch.ldexp(torch.ones((), dtype=torch.float32, device=dev), e)
+        return val * s.repeat_interleave(32, dim=1)
+
+    def dequantize(self) -> torch.Tensor:
+        """bf16 fragment-major weight with the same values (exact: e2m1 times a power of two)."""
+        return tile_weight(self.dequantize_f32().to(torch.bfloat16))
+
+
+def quantize_mxfp4(wt: torch.Tensor) -> Mx4Weight:
+    """bf16 fragment-major weight -> Mx4Weight.  Per 32-element block along K of one output
+    row: scale 2^(floor(log2(amax)) - 2) (e8m0, bias 127; an all-zero block gets 127),
+    elements rounded to the nearest e2m1 value with ties to even, saturating at +-6."""
+    dev = wt.device
+    w = untile_weight(wt).float()
+    N, K = w.shape
+    assert K % 128 == 0, "mxfp4 weights need K % 128 == 0 (four k-steps per 16-byte load)"
+    assert N % 16 == 0, (N, K)
+    blk = w.reshape(N, K // 32, 32)
+    amax = blk.abs().amax(-1)
+    e = torch.frexp(amax)[1] - 3  # frexp: amax = m * 2^ex, m in [0.5, 1) -> floor(log2) = ex - 1
+    byte = torch.where(amax > 0, (e + 127).clamp(1, 254), torch.full_like(e, 127))
+    v = blk / torch.ldexp(torch.ones((), dtype=torch.float32, device=dev), byte - 127)[..., None]
+    a = v.abs().clamp(max=6.0)
+    # spacing 0.5 below 2, 1 below 4, 2 above; torch.round is half-to-even, which is the even
+    # code of every tie on this grid
+    qa = torch.where(a < 2, torch.round(a * 2) / 2, torch.where(a < 4, torch.round(a), torch.round(a / 2) * 2))
+    code = torch.where(qa <= 2, qa * 2, torch.where(qa <= 4, qa + 2, qa / 2 + 4)).to(torch.uint8)
+    code = (code | ((v < 0).to(torch.uint8) << 3)).reshape(N, K)
+    G, P = N // 16, K // 128
+    t = tile_weight(code)  # [G, 4P, 64, 8]: a lane's 8 codes of one k-step
+    words = (t[..., 0::2] | (t[..., 1::2] << 4))  # [G, 4P, 64, 4] bytes of one 32-bit word
+    data = words.reshape(G, P, 4, 64, 4).permute(0, 1, 3, 2, 4).contiguous().reshape(G, P, 64, 16)
+    scale = byte.to(torch.uint8).reshape(G, 16, P, 4).permute(0, 2, 1, 3).contiguous()
+    return Mx4Weight(data, scale)
+
+
+def _fmt(wt) -> str:
+    """Storage format of a projection weight: "bf16" (a tensor), "fp8" or "mx4"."""
+    return "mx4" if isinstance(wt, Mx4Weight) else "fp8" if isinstance(wt, Fp8Weight) else "bf16"
+
+
 def _is_f8(wt) -> bool:
-    return isinstance(wt, Fp8Weight)
+    return _fmt(wt) == "fp8"
 
 
 def _wptr(wt):
-    return (wt.data.data_ptr(), wt.scale.data_ptr()) if _is_f8(wt) else (wt.data_ptr(), None)
+    """(weights or codes, scales or None) device pointers."""
+    return (wt.data_ptr(), None) if _fmt(wt) == "bf16" else (wt.data.data_ptr(), wt.scale.data_ptr())
+
+
+# Launch codes of the MXFP4 kernel: waves | U << 8 | NG << 16 (split-K waves, super-steps per
+# weight batch, column groups per wave).  Its ladder serves a subset (mx4_code_ok).
+MX4_CODES = [w | (u << 8) | (ng << 16) for w in (1, 2, 4, 8) for u in (1, 4, 8) for ng in (1, 2, 4)]
+
+
+def mx4_code_ok(M: int, K: int, N: int, epi: int, norm: bool, code: int) -> bool:
+    """Does the MXFP4 kernel's launch ladder serve this shape with this launch code?"""
+    return bool(_lib.lib().p2p_mx4_gemm_ok(M, K, N, int(epi), int(bool(norm)), int(code)))
 
 
 def m_tile(M: int) -> int:
@@ -108,7 +210,7 @@ def m_tile(M: int) -> int:
 def tune_key(wt, M, epi, norm):
     N, K = tiled_shape(wt)
     key = (N, K, int(epi), bool(norm), m_tile(min(M, SKINNY_MAX_M)))
-    return key + ("fp8",) if _is_f8(wt) else key
+    return key if _fmt(wt) == "bf16" else key + (_fmt(wt),)
 
 
 def set_tune(key, code: int):
@@ -216,7 +318,7 @@ def pack_frag(x: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
 
 
 def _want_tiled(wt, M, N, K, epi, norm, waves) -> bool:
-    if _is_f8(wt):  # FP8 weights run on the skinny kernel only (M chunks of 64)
+    if _fmt(wt) != "bf16":  # FP8 / MXFP4 weights: their skinny kernel only (M chunks of 64)
         return False
     if use_tiled(M, N, K, epi):
         return True
@@ -294,7 +396,7 @@ def fold_norm(w: torch.Tensor, gain: torch.Tensor) -> torch.Tensor:
 
 def _ref(wt, x, epi, norm, out, eps):
     N, K = tiled_shape(wt)
-    W = wt.dequantize_f32() if _is_f8(wt) else untile_weight(wt).float()
+    W = untile_weight(wt).float() if _fmt(wt) == "bf16" else wt.dequantize_f32()
     xf = x.float()
     acc = xf @ W.t()
     if norm:
@@ -335,7 +437,7 @@ def skinny_gemm(wt: torch.Tensor, x: torch.Tensor, epi: int = EPI_STORE, norm: b
     assert x.stride(1) == 1 and out.stride(1) == 1
     L = _lib.lib()
     s = _lib.stream_ptr(x.device)
-    if (epi == EPI_SILU and norm and M > SKINNY_MAX_M and TALL_SILU and not _is_f8(wt)
+    if (epi == EPI_SILU and norm and M > SKINNY_MAX_M and TALL_SILU and _fmt(wt) == "bf16"
             and not (waves & TILED_FLAG) and tall_silu_ok(M, K, N)):
         # batched-prompt gate_up: all rows in one workgroup, weights streamed once (tall_gemm.hip)
         _lib.check(_lib.experimental().p2p_tall_silu(wt.data_ptr(), x.data_ptr(), x.stride(0), M, K, N,
@@ -352,6 +454,11 @@ def skinny_gemm(wt: torch.Tensor, x: torch.Tensor, epi: int = EPI_STORE, norm: b
         os_ = out[m0:m0 + mc]
         wp, sp = _wptr(wt)
         code = _code(wt, mc, epi, norm, waves)
+        if _fmt(wt) == "mx4":  # its own kernel and launch codes (mx4_gemm.hip)
+            _lib.check(L.p2p_mx4_gemm(wp, sp, xs.data_ptr(), x.stride(0), mc, K, N, epi, int(norm),
+                                      os_.data_ptr(), out.stride(0), float(eps), code, s),
+                       "mx4_gemm")
+            continue
         if code & PERSIST_FLAG:
             _lib.experimental()  # the persistent GEMV's library (its symbol, found by dlsym)
         if code & AFRAG_FLAG and not x_packed:
@@ -442,6 +549,13 @@ def qkv_rope_gemm(wt, x, pos, slots, cos_sin, n_heads, n_kv, q_out, k_cache, v_c
         wp, sp = _wptr(wt)
         code = _code(wt, mc, EPI_QKV_ROPE, True, waves)
         xs = x[m0:m0 + mc]
+        if _fmt(wt) == "mx4":
+            _lib.check(L.p2p_mx4_gemm_qkv_rope(
+                wp, sp, xs.data_ptr(), x.stride(0), mc, K, n_heads, n_kv,
+                pos[m0:].data_ptr(), slots[m0:].data_ptr(), cos_sin.data_ptr(),
+                q_out[m0:].data_ptr(), q_out.stride(0), k_cache.data_ptr(), v_cache.data_ptr(),
+                float(eps), code, s), "mx4_gemm_qkv_rope")
+            continue
         if code & AFRAG_FLAG:
             xs = _packed(xs)
         _lib.check(L.p2p_skinny_gemm_qkv_rope(
@@ -479,6 +593,8 @@ def lm_head_argmax(wt, x, keys, col_offset: int = 0, eps: float = 1e-5, waves: i
         cur = keys[:M, 0]
         keys[:M, 0] = torch.where((k ^ sign) > (cur ^ sign), k, cur)
         return keys
+    if _fmt(wt) == "mx4":
+        raise TypeError("lm_head_argmax: no MXFP4 LM head (bf16 or FP8 weights)")
     L = _lib.lib()
     if _want_tiled(wt, M, N, K, EPI_ARGMAX, True, waves):
         _lib.check(L.p2p_tiled_gemm_argmax(wt.data_ptr(), x.data_ptr(), x.stride(0), M, K, N,
