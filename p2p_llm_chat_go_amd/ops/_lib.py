@@ -99,6 +99,13 @@ _SIGS = {
                               c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
                               c_float, c_int, c_void_p],
     "p2p_mx4_gemm_ok": [c_int, c_int, c_int, c_int, c_int, c_int],
+    # MXFP4 prefill GEMM (mx4_prefill_gemm.hip, M > 64): the same argument lists
+    "p2p_mx4_prefill_gemm": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                             c_int, c_void_p, c_int, c_float, c_int, c_void_p],
+    "p2p_mx4_prefill_gemm_qkv_rope": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                                      c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                      c_void_p, c_void_p, c_float, c_int, c_void_p],
+    "p2p_mx4_prefill_ok": [c_int, c_int, c_int, c_int, c_int, c_int],
     "p2p_sample": [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                    c_void_p, c_void_p],
     "p2p_topk_candidates": [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p],

@@ -201,6 +201,47 @@ def mx4_code_ok(M: int, K: int, N: int, epi: int, norm: bool, code: int) -> bool
     return bool(_lib.lib().p2p_mx4_gemm_ok(M, K, N, int(epi), int(bool(norm)), int(code)))
 
 
+# launch-code bit: the MXFP4 prefill kernel (csrc/kernels/mx4_prefill_gemm.hip: one 8-wave
+# workgroup per BM x BN tile over the whole K, M > 64); bits 0..3 = BM / 64, bits 4..7 =
+# BN / 64.  The bit above TILED_FLAG .. PERSIST_FLAG (24..28), so a prefill code is never
+# taken for a skinny MX4_CODES entry (those stay below bit 24)
+MX4_PREFILL_FLAG = 1 << 29
+MX4_PREFILL_CODES = [MX4_PREFILL_FLAG | (bm // 64) | ((bn // 64) << 4)
+                     for bm in (64, 128, 256, 512) for bn in (64, 128)]  # 512 rows: not served
+
+
+def mx4_prefill_ok(M: int, K: int, N: int, epi: int, norm: bool, code: int = 0) -> bool:
+    """Does the MXFP4 prefill kernel serve this shape with this tile code (0 = its default)?"""
+    if code and not code & MX4_PREFILL_FLAG:
+        return False
+    return bool(_lib.lib().p2p_mx4_prefill_ok(M, K, N, int(epi), int(bool(norm)), int(code) & 0xff))
+
+
+def mx4_route(M: int, K: int, N: int, epi: int, norm: bool) -> str:
+    """Which kernel an MXFP4 projection of M rows runs on with no explicit launch code:
+    "prefill" (mx4_prefill_gemm.hip, one launch) or "skinny" (mx4_gemm.hip, one launch per
+    64 rows).  Pure: the shape rules of the prefill kernel and the measured thresholds."""
+    if M <= SKINNY_MAX_M or K % 128 or N % (32 if epi == EPI_SILU else 16):
+        return "skinny"
+    if epi not in (EPI_STORE, EPI_RESID, EPI_SILU, EPI_F32, EPI_QKV_ROPE):
+        return "skinny"
+    if epi == EPI_QKV_ROPE and not norm:
+        return "skinny"
+    if M <= 96 and (N, K) not in _MX4_PREFILL_96:
+        return "skinny"
+    return "prefill"
+
+
+# profiles/mx4_prefill_gemm.jsonl (bench/mx4_prefill_bench.py; llama3.1-8B and -70B projections,
+# 96..1024 rows, cold weights; the two passes of one record differed by 5.8 % at most, 0.75 % in
+# the median).  From 128 rows the prefill kernel's best tile beat the 64-row chunks at every
+# shape, 1.08x (70B down, 128 rows) to 7.9x (8B o, 1024 rows).  At 96 rows it won only at
+# these (N, K), 1.22x .. 1.58x; 8B qkv and 70B o tied within the spread (0.98x, 1.02x) and
+# down lost (0.92x 8B, 0.87x 70B: K is long and the grid 128 tiles), so 65..96 rows of any
+# other shape keep the chunks.
+_MX4_PREFILL_96 = {(4096, 4096), (28672, 4096), (10240, 8192), (57344, 8192)}
+
+
 def m_tile(M: int) -> int:
     """Autotune bucket of M: 16-row MFMA tiles (1..4).  The skinny kernel runs 3 tiles as
     4; the midm / tiled kernels use the exact count, so 33-48 rows tune separately."""
@@ -318,13 +359,22 @@ def pack_frag(x: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
 
 
 def _want_tiled(wt, M, N, K, epi, norm, waves) -> bool:
-    if _fmt(wt) != "bf16":  # FP8 / MXFP4 weights: their skinny kernel only (M chunks of 64)
+    if _fmt(wt) != "bf16":  # FP8: the skinny kernel in M chunks of 64; MXFP4: _mx4_prefill
         return False
     if use_tiled(M, N, K, epi):
         return True
     if M > SKINNY_MAX_M or not tiled_ok(N, K, epi):
         return False
     return bool(_code(wt, M, epi, norm, waves) & TILED_FLAG)
+
+
+def _mx4_prefill(M, K, N, epi, norm, waves) -> bool:
+    """An MXFP4 projection goes to the prefill kernel on an explicit prefill code (a code its
+    ladder does not serve then fails the launch) or, with no code, where mx4_route says so;
+    a skinny code keeps the 64-row chunks."""
+    if waves:
+        return bool(waves & MX4_PREFILL_FLAG)
+    return mx4_route(M, K, N, epi, norm) == "prefill"
 
 
 def tiled_config(version: int = 2, tile: int = 0, splitk: int = 0):
@@ -420,7 +470,8 @@ def _ref(wt, x, epi, norm, out, eps):
 def skinny_gemm(wt: torch.Tensor, x: torch.Tensor, epi: int = EPI_STORE, norm: bool = False,
                 out: torch.Tensor | None = None, eps: float = 1e-5, waves: int = 0,
                 x_packed: bool = False) -> torch.Tensor:
-    """out = epi(rstd(x) * x @ W^T) for x [M, K] with M <= 64 (rows > 64 are chunked).
+    """out = epi(rstd(x) * x @ W^T) for x [M, K] with M <= 64 (rows > 64 are chunked, or run
+    the tiled / MXFP4 prefill kernel where the weight format has one: _want_tiled, mx4_route).
     A launch code with AFRAG_FLAG packs x fragment-major first (pack_frag) unless
     ``x_packed`` says the caller already did (then x is pack_frag's output, rows <= 64)."""
     N, K = tiled_shape(wt)
@@ -447,6 +498,12 @@ def skinny_gemm(wt: torch.Tensor, x: torch.Tensor, epi: int = EPI_STORE, norm: b
         _lib.check(L.p2p_tiled_gemm(wt.data_ptr(), x.data_ptr(), x.stride(0), M, K, N, epi,
                                     int(norm), out.data_ptr(), out.stride(0), float(eps), s),
                    "tiled_gemm")
+        return out
+    if _fmt(wt) == "mx4" and _mx4_prefill(M, K, N, epi, norm, waves):
+        wp, sp = _wptr(wt)
+        _lib.check(L.p2p_mx4_prefill_gemm(wp, sp, x.data_ptr(), x.stride(0), M, K, N, epi,
+                                          int(norm), out.data_ptr(), out.stride(0), float(eps),
+                                          waves & 0xff, s), "mx4_prefill_gemm")
         return out
     for m0 in range(0, M, SKINNY_MAX_M):
         mc = min(SKINNY_MAX_M, M - m0)
@@ -543,6 +600,14 @@ def qkv_rope_gemm(wt, x, pos, slots, cos_sin, n_heads, n_kv, q_out, k_cache, v_c
             wt.data_ptr(), x.data_ptr(), x.stride(0), M, K, n_heads, n_kv, pos.data_ptr(),
             slots.data_ptr(), cos_sin.data_ptr(), q_out.data_ptr(), q_out.stride(0),
             k_cache.data_ptr(), v_cache.data_ptr(), float(eps), s), "tiled_gemm_qkv_rope")
+        return q_out
+    if _fmt(wt) == "mx4" and _mx4_prefill(M, K, N, EPI_QKV_ROPE, True, waves):
+        wp, sp = _wptr(wt)
+        _lib.check(L.p2p_mx4_prefill_gemm_qkv_rope(
+            wp, sp, x.data_ptr(), x.stride(0), M, K, n_heads, n_kv, pos.data_ptr(),
+            slots.data_ptr(), cos_sin.data_ptr(), q_out.data_ptr(), q_out.stride(0),
+            k_cache.data_ptr(), v_cache.data_ptr(), float(eps), waves & 0xff, s),
+            "mx4_prefill_gemm_qkv_rope")
         return q_out
     for m0 in range(0, M, SKINNY_MAX_M):
         mc = min(SKINNY_MAX_M, M - m0)
