@@ -69,7 +69,8 @@ class Engine:
         self.device = torch.device(device)
         own = weights is None
         # weight_dtype "fp8": weight-only e4m3 dense projections (EngineWeights.quantize_fp8);
-        # "mxfp4": weight-only OCP MXFP4 projections + FP8 LM head (EngineWeights.quantize_mxfp4)
+        # "mxfp4": weight-only OCP MXFP4 projections and MoE experts + FP8 LM head
+        # (EngineWeights.quantize_mxfp4)
         self.weight_dtype = weight_dtype or os.environ.get("ENGINE_WEIGHTS", "bf16")
         if self.weight_dtype == "mxfp4" and max(tp_size, 1 if own else weights.tp_size) > 1:
             raise ValueError("weight_dtype mxfp4 runs on one GPU only (tp_size 1): the fused "

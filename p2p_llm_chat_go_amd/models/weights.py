@@ -95,11 +95,12 @@ class EngineWeights:
             self.lm_head = ops.quantize_fp8(self.lm_head)
         return self
 
-    def quantize_mxfp4(self, names=("qkv", "o", "gate_up", "down")) -> "EngineWeights":
+    def quantize_mxfp4(self, names=("qkv", "o", "gate_up", "down", "w13", "w2")) -> "EngineWeights":
         """Weight-only MXFP4 (OCP e2m1 codes, one e8m0 scale per 32 elements along K: 4.25
-        bits per weight) for the dense projections, in place; the LM head goes to the FP8
-        path (a 4-bit LM head costs quality for 3 % of the bytes).  The embedding, router and
-        MoE experts stay bf16.  Opt-in (ENGINE_WEIGHTS=mxfp4)."""
+        bits per weight) for the dense projections and the MoE experts (stacked, one
+        grouped launch per expert GEMM), in place; the LM head goes to the FP8 path (a 4-bit
+        LM head costs quality for 3 % of the bytes).  The embedding and the router stay
+        bf16.  Opt-in (ENGINE_WEIGHTS=mxfp4)."""
         for lw in self.layers:
             for name in names:
                 t = getattr(lw, name)

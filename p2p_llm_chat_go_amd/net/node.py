@@ -20,7 +20,8 @@ STRICT_SENDER, UI_FILE) and the engine knobs:
   ENGINE_TP       tensor-parallel ranks per replica (default 1; 8 for 70B over xGMI)
   ENGINE_EP       expert-parallel ranks per replica (MoE models, default 1)
   ENGINE_WEIGHTS  bf16 (default) / fp8 (weight-only e4m3 projections) / mxfp4 (weight-only
-                  OCP MXFP4 projections, 4.25 bits per weight, FP8 LM head; ENGINE_TP=1 only)
+                  OCP MXFP4 projections and MoE experts, 4.25 bits per weight, FP8 LM head;
+                  ENGINE_TP=1 only)
   ENGINE_NATIVE_LOOP  1 (default) / 0: single-GPU replicas run the C++ step loop
                   (engine.native_loop) instead of the Python one
   ENGINE_TIMEOUT  per-request deadline in seconds (default 60, the reference UI's bound)

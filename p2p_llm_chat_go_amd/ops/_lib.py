@@ -121,6 +121,12 @@ _SIGS = {
     "p2p_grouped_gemm": [c_void_p, ctypes.c_longlong, c_int, c_void_p, c_void_p, c_int, c_int,
                          c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
                          c_int, c_float, c_int, c_void_p],
+    # MXFP4 grouped GEMM (mx4_moe_gemm.hip): codes, scales and their per-expert byte strides,
+    # then as p2p_grouped_gemm from n_experts on
+    "p2p_mx4_grouped_gemm": [c_void_p, c_void_p, ctypes.c_longlong, ctypes.c_longlong, c_int,
+                             c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int,
+                             c_int, c_int, c_int, c_int, c_void_p, c_int, c_float, c_int, c_void_p],
+    "p2p_mx4_grouped_ok": [c_int, c_int, c_int, c_int, c_int, c_int],
     "p2p_moe_route": [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
                       c_void_p, c_void_p, c_int, c_void_p],
     "p2p_moe_router_route": [c_void_p, c_int, c_int, c_int, c_void_p, c_float, c_int, c_int, c_int,

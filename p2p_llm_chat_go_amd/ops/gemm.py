@@ -105,7 +105,11 @@ class Mx4Weight:
               16g + r for k-steps 4p .. 4p + 3.
 
     ``shape`` is the fragment-major shape of the bf16 weight it stands for (``tiled_shape``
-    and the engine's shape arithmetic work unchanged).  Not a ``torch.Tensor``."""
+    and the engine's shape arithmetic work unchanged).  Not a ``torch.Tensor``.
+
+    A stack of MoE experts carries a leading expert dimension on both planes (``[E, N/16,
+    ...]``, what ``csrc/kernels/mx4_moe_gemm.hip`` streams); ``wt[e]`` is expert e's
+    ``Mx4Weight`` (views, no copy)."""
 
     def __init__(self, data: torch.Tensor, scale: torch.Tensor):
         self.data = data
@@ -113,8 +117,12 @@ class Mx4Weight:
 
     @property
     def shape(self):
-        G, P = self.data.shape[0], self.data.shape[1]
-        return torch.Size((G, 4 * P, 64, 8))
+        *lead, G, P = self.data.shape[:-2]
+        return torch.Size((*lead, G, 4 * P, 64, 8))
+
+    def __getitem__(self, e: int) -> "Mx4Weight":
+        assert self.data.dim() == 5, "not a stack of experts"
+        return Mx4Weight(self.data[e], self.scale[e])
 
     @property
     def device(self):
@@ -133,7 +141,10 @@ class Mx4Weight:
         return self.data.numel() + self.scale.numel()
 
     def dequantize_f32(self) -> torch.Tensor:
-        """Exact fp32 [N, K] (natural layout) values the kernel multiplies with."""
+        """Exact fp32 [N, K] (natural layout; [E, N, K] of a stack) values the kernel
+        multiplies with."""
+        if self.data.dim() == 5:
+            return torch.stack([self[e].dequantize_f32() for e in range(self.data.shape[0])])
         G, P = self.data.shape[0], self.data.shape[1]
         dev = self.data.device
         d = self.data.reshape(G, P, 64, 4, 4).permute(0, 1, 3, 2, 4).reshape(G, 4 * P, 64, 4)
@@ -146,13 +157,26 @@ class Mx4Weight:
 
     def dequantize(self) -> torch.Tensor:
         """bf16 fragment-major weight with the same values (exact: e2m1 times a power of two)."""
+        if self.data.dim() == 5:
+            return torch.stack([self[e].dequantize() for e in range(self.data.shape[0])])
         return tile_weight(self.dequantize_f32().to(torch.bfloat16))
 
 
 def quantize_mxfp4(wt: torch.Tensor) -> Mx4Weight:
     """bf16 fragment-major weight -> Mx4Weight.  Per 32-element block along K of one output
     row: scale 2^(floor(log2(amax)) - 2) (e8m0, bias 127; an all-zero block gets 127),
-    elements rounded to the nearest e2m1 value with ties to even, saturating at +-6."""
+    elements rounded to the nearest e2m1 value with ties to even, saturating at +-6.
+    A stacked [E, N/16, K/32, 64, 8] weight (MoE experts) is quantized expert by expert, so
+    the fp32 temporaries stay one expert large, into a stacked Mx4Weight."""
+    if wt.dim() == 5:
+        E, G, S = wt.shape[:3]
+        assert S % 4 == 0, "mxfp4 weights need K % 128 == 0 (four k-steps per 16-byte load)"
+        out = Mx4Weight(torch.empty(E, G, S // 4, 64, 16, dtype=torch.uint8, device=wt.device),
+                        torch.empty(E, G, S // 4, 16, 4, dtype=torch.uint8, device=wt.device))
+        for e in range(E):
+            q = quantize_mxfp4(wt[e])
+            out.data[e], out.scale[e] = q.data, q.scale
+        return out
     dev = wt.device
     w = untile_weight(wt).float()
     N, K = w.shape

@@ -1,8 +1,9 @@
 """Sparse-MoE ops (Mixtral): routing, grouped expert GEMMs, combine.
 
 The expert GEMMs are the grouped mode of the skinny MFMA kernel
-(``csrc/kernels/skinny_gemm.hip``): one launch covers all local experts
-(grid.y), each expert reads its weights only if at least one row was routed to
+(``csrc/kernels/skinny_gemm.hip``), or the MXFP4 grouped kernel
+(``csrc/kernels/mx4_moe_gemm.hip``) for 4-bit experts: one launch covers all local
+experts, each expert reads its weights only if at least one row was routed to
 it -- at decode batch 1 Mixtral streams 2 of its 8 experts per layer.
 Slots: a token r routed to its k-th expert is slot r*top_k + k.
 """
@@ -11,7 +12,7 @@ from __future__ import annotations
 import torch
 
 from . import _lib
-from .gemm import EPI_SILU, EPI_STORE, _ref, tiled_shape
+from .gemm import EPI_SILU, EPI_STORE, Mx4Weight, _ref, tiled_shape
 
 
 def moe_route(logits, E, K, e_lo, e_local, topk_ids, topk_w, cnt, rows):
@@ -69,10 +70,13 @@ def moe_router_logits(h, wr, E, logits, eps=1e-5):
     return logits
 
 
-def grouped_gemm(wt, cnt, rows, x, x_div, max_rows, epi, out, norm=False, row_w=None, eps=1e-5):
+def grouped_gemm(wt, cnt, rows, x, x_div, max_rows, epi, out, norm=False, row_w=None, eps=1e-5,
+                 code=0):
     """Per local expert e: out[slot] = epi(x[slot // x_div] @ W_e^T) for its routed slots.
 
-    wt: [E_local, N/16, K/32, 64, 8] tiled expert weights.
+    wt: [E_local, N/16, K/32, 64, 8] tiled expert weights, or a stacked ``Mx4Weight`` (the
+    MXFP4 grouped kernel, ``csrc/kernels/mx4_moe_gemm.hip``, for any max_rows; ``code`` is its
+    launch code, waves | U << 8 | NG << 16, 0 = default).
     """
     E = wt.shape[0]
     N, K = tiled_shape(wt[0])
@@ -91,12 +95,24 @@ def grouped_gemm(wt, cnt, rows, x, x_div, max_rows, epi, out, norm=False, row_w=
             out[slots] = o
         return out
     L = _lib.lib()
+    if isinstance(wt, Mx4Weight):
+        _lib.check(L.p2p_mx4_grouped_gemm(
+            wt.data.data_ptr(), wt.scale.data_ptr(), wt.data.stride(0), wt.scale.stride(0), E,
+            cnt.data_ptr(), rows.data_ptr(), rows.stride(0), x_div, _lib.ptr(row_w), x.data_ptr(),
+            x.stride(0), max_rows, K, N, epi, int(norm), out.data_ptr(), out.stride(0), float(eps),
+            int(code), _lib.stream_ptr(x.device)), "mx4_grouped_gemm")
+        return out
     w_stride = wt[0].numel() // 8  # in bf16x8 units
     _lib.check(L.p2p_grouped_gemm(wt.data_ptr(), w_stride, E, cnt.data_ptr(), rows.data_ptr(),
                                   rows.stride(0), x_div, _lib.ptr(row_w), x.data_ptr(), x.stride(0),
                                   max_rows, K, N, epi, int(norm), out.data_ptr(), out.stride(0),
                                   float(eps), 0, _lib.stream_ptr(x.device)), "grouped_gemm")
     return out
+
+
+def mx4_grouped_ok(max_rows: int, K: int, N: int, epi: int, norm: bool, code: int = 0) -> bool:
+    """Does the MXFP4 grouped kernel's ladder serve this shape with this launch code?"""
+    return bool(_lib.lib().p2p_mx4_grouped_ok(max_rows, K, N, int(epi), int(bool(norm)), int(code)))
 
 
 def moe_combine(o, topk_ids, R, K, e_lo, e_local, out, accumulate=True):
