@@ -15,6 +15,7 @@ from .attention import (PAGE, HEAD_DIM, attn_oproj, attn_oproj_ok, attn_oproj_he
                         attn_oproj_heads_ok, attn_oproj_heads_workspace, attn_workspace,
                         flash_prefill, flash_tile, paged_attention, prefill_tiles, rope_cache,
                         qkv_attn, qkv_attn_ok, qkv_attn_oproj_ok, qkv_attn_workspace)
+from .moe import mx4_grouped_ok, mx4_grouped_prefill_ok, mx4_grouped_route
 from .elementwise import advance, argmax, gather_rows, l3_prefetch
 from .sampling import sample, sample_candidates, topk_candidates
 from ._lib import available as kernels_available, lib as kernel_lib, lib_path as kernel_lib_path
@@ -22,6 +23,7 @@ from ._lib import available as kernels_available, lib as kernel_lib, lib_path as
 __all__ = [
     "Mx4Weight", "quantize_mxfp4", "MX4_CODES", "mx4_code_ok",
     "MX4_PREFILL_CODES", "MX4_PREFILL_FLAG", "mx4_prefill_ok", "mx4_route",
+    "mx4_grouped_ok", "mx4_grouped_prefill_ok", "mx4_grouped_route",
     "EPI_AR", "skinny_ar_ok", "skinny_gemm_ar", "EPI_F32", "EPI_RESID", "EPI_SILU", "EPI_STORE", "fold_norm", "skinny_gemm", "tile_weight",
     "tiled_shape", "untile_weight", "argmax_finalize", "lm_head_argmax", "new_argmax_keys", "qkv_rope_gemm",
     "rope_row_perm", "PAGE", "HEAD_DIM", "attn_workspace", "paged_attention", "flash_prefill", "flash_tile", "prefill_tiles",

@@ -127,6 +127,12 @@ _SIGS = {
                              c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int,
                              c_int, c_int, c_int, c_int, c_void_p, c_int, c_float, c_int, c_void_p],
     "p2p_mx4_grouped_ok": [c_int, c_int, c_int, c_int, c_int, c_int],
+    # MXFP4 grouped prefill GEMM (mx4_moe_prefill_gemm.hip, max_rows > 64): the same lists
+    "p2p_mx4_grouped_prefill_gemm": [c_void_p, c_void_p, ctypes.c_longlong, ctypes.c_longlong,
+                                     c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
+                                     c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int,
+                                     c_float, c_int, c_void_p],
+    "p2p_mx4_grouped_prefill_ok": [c_int, c_int, c_int, c_int, c_int, c_int],
     "p2p_moe_route": [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
                       c_void_p, c_void_p, c_int, c_void_p],
     "p2p_moe_router_route": [c_void_p, c_int, c_int, c_int, c_void_p, c_float, c_int, c_int, c_int,

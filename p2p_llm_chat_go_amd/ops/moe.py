@@ -1,9 +1,9 @@
 """Sparse-MoE ops (Mixtral): routing, grouped expert GEMMs, combine.
 
 The expert GEMMs are the grouped mode of the skinny MFMA kernel
-(``csrc/kernels/skinny_gemm.hip``), or the MXFP4 grouped kernel
-(``csrc/kernels/mx4_moe_gemm.hip``) for 4-bit experts: one launch covers all local
-experts, each expert reads its weights only if at least one row was routed to
+(``csrc/kernels/skinny_gemm.hip``), or the MXFP4 grouped kernels for 4-bit experts
+(``csrc/kernels/mx4_moe_gemm.hip``, 64-row windows, and ``mx4_moe_prefill_gemm.hip``, LDS
+tiles for prompt chunks; ``mx4_grouped_route``): one launch covers all local experts, each expert reads its weights only if at least one row was routed to
 it -- at decode batch 1 Mixtral streams 2 of its 8 experts per layer.
 Slots: a token r routed to its k-th expert is slot r*top_k + k.
 """
@@ -12,7 +12,7 @@ from __future__ import annotations
 import torch
 
 from . import _lib
-from .gemm import EPI_SILU, EPI_STORE, Mx4Weight, _ref, tiled_shape
+from .gemm import EPI_SILU, EPI_STORE, MX4_PREFILL_FLAG, Mx4Weight, _ref, tiled_shape
 
 
 def moe_route(logits, E, K, e_lo, e_local, topk_ids, topk_w, cnt, rows):
@@ -75,8 +75,10 @@ def grouped_gemm(wt, cnt, rows, x, x_div, max_rows, epi, out, norm=False, row_w=
     """Per local expert e: out[slot] = epi(x[slot // x_div] @ W_e^T) for its routed slots.
 
     wt: [E_local, N/16, K/32, 64, 8] tiled expert weights, or a stacked ``Mx4Weight`` (the
-    MXFP4 grouped kernel, ``csrc/kernels/mx4_moe_gemm.hip``, for any max_rows; ``code`` is its
-    launch code, waves | U << 8 | NG << 16, 0 = default).
+    MXFP4 grouped kernels).  ``code`` picks the MXFP4 launch: one of ``MX4_PREFILL_CODES``
+    (``MX4_PREFILL_FLAG`` set) is a tile of the prefill kernel, ``mx4_moe_prefill_gemm.hip``,
+    max_rows > 64; any other non-zero code is the window kernel's (``mx4_moe_gemm.hip``, any
+    max_rows) waves | U << 8 | NG << 16; 0 asks ``mx4_grouped_route``.
     """
     E = wt.shape[0]
     N, K = tiled_shape(wt[0])
@@ -96,11 +98,17 @@ def grouped_gemm(wt, cnt, rows, x, x_div, max_rows, epi, out, norm=False, row_w=
         return out
     L = _lib.lib()
     if isinstance(wt, Mx4Weight):
-        _lib.check(L.p2p_mx4_grouped_gemm(
+        code = int(code)
+        if code & MX4_PREFILL_FLAG or (
+                code == 0 and mx4_grouped_route(max_rows, K, N, epi, norm) == "prefill"):
+            fn, what, code = L.p2p_mx4_grouped_prefill_gemm, "mx4_grouped_prefill_gemm", code & 0xff
+        else:
+            fn, what = L.p2p_mx4_grouped_gemm, "mx4_grouped_gemm"
+        _lib.check(fn(
             wt.data.data_ptr(), wt.scale.data_ptr(), wt.data.stride(0), wt.scale.stride(0), E,
             cnt.data_ptr(), rows.data_ptr(), rows.stride(0), x_div, _lib.ptr(row_w), x.data_ptr(),
             x.stride(0), max_rows, K, N, epi, int(norm), out.data_ptr(), out.stride(0), float(eps),
-            int(code), _lib.stream_ptr(x.device)), "mx4_grouped_gemm")
+            code, _lib.stream_ptr(x.device)), what)
         return out
     w_stride = wt[0].numel() // 8  # in bf16x8 units
     _lib.check(L.p2p_grouped_gemm(wt.data_ptr(), w_stride, E, cnt.data_ptr(), rows.data_ptr(),
@@ -113,6 +121,37 @@ def grouped_gemm(wt, cnt, rows, x, x_div, max_rows, epi, out, norm=False, row_w=
 def mx4_grouped_ok(max_rows: int, K: int, N: int, epi: int, norm: bool, code: int = 0) -> bool:
     """Does the MXFP4 grouped kernel's ladder serve this shape with this launch code?"""
     return bool(_lib.lib().p2p_mx4_grouped_ok(max_rows, K, N, int(epi), int(bool(norm)), int(code)))
+
+
+def mx4_grouped_prefill_ok(max_rows: int, K: int, N: int, epi: int, norm: bool,
+                           code: int = 0) -> bool:
+    """Does the MXFP4 grouped prefill kernel serve this shape with this tile code (one of
+    ``MX4_PREFILL_CODES``; 0 = its default)?"""
+    if code and not code & MX4_PREFILL_FLAG:
+        return False
+    return bool(_lib.lib().p2p_mx4_grouped_prefill_ok(max_rows, K, N, int(epi), int(bool(norm)),
+                                                      int(code) & 0xff))
+
+
+# profiles/mx4_moe_prefill_gemm.jsonl (bench/mx4_moe_prefill_bench.py; Mixtral-8x7B w13 and w2,
+# 96 .. 1024 tokens x top-2 over 8 experts, cold weights; the two passes of one record differed
+# by 2.7 % at most).  The prefill kernel's default tile beat the window kernel at every measured
+# token count, 1.34x (w2, 192 tokens) to 6.4x (w2, 1024 tokens), always by more than the
+# record's spread.  65 .. 95 tokens were not measured and keep the window kernel.
+_MX4_GROUPED_PREFILL_MIN = 96
+
+
+def mx4_grouped_route(max_rows: int, K: int, N: int, epi: int, norm: bool) -> str:
+    """Which kernel a grouped MXFP4 launch runs on with no explicit code: "prefill"
+    (mx4_moe_prefill_gemm.hip) or "window" (mx4_moe_gemm.hip).  Pure: the shape rules of the
+    prefill kernel and the measured threshold; max_rows <= 64 always stays on the windows."""
+    if max_rows <= 64 or max_rows < _MX4_GROUPED_PREFILL_MIN:
+        return "window"
+    if K <= 0 or K % 128 or N <= 0 or N % (32 if epi == EPI_SILU else 16):
+        return "window"
+    if not ((epi == EPI_SILU and norm) or (epi == EPI_STORE and not norm)):
+        return "window"
+    return "prefill"
 
 
 def moe_combine(o, topk_ids, R, K, e_lo, e_local, out, accumulate=True):
