@@ -149,7 +149,11 @@ def autotune_model(model, batch_sizes=(1,), verbose=False, table: dict | None = 
     dev = model.device
     H = cfg.hidden
     nq, nkv = model.nq, model.nkv
-    kc, vc = model.kv.layer(0)
+    # an FP8 KV cache runs the qkv projection with the plain store epilogue (the quantising
+    # write is a kernel of its own): tune that launch, and never hand e4m3 pages to the
+    # QKV_ROPE epilogue, which writes bf16
+    kv_fp8 = model.kv.kv_dtype == "fp8"
+    kc, vc = (None, None) if kv_fp8 else model.kv.layer(0)
     result = {}
     layers = w.layers
     for M in sorted(set(min(b, G.SKINNY_MAX_M) for b in batch_sizes)):
@@ -164,6 +168,11 @@ def autotune_model(model, batch_sizes=(1,), verbose=False, table: dict | None = 
                                                  waves=c)),
                 ("o_proj", [lw.o for lw in layers], G.EPI_RESID,
                  lambda wt, c: ops.skinny_gemm(wt, q, ops.EPI_RESID, out=h, waves=c))]
+        if kv_fp8:
+            qkv = torch.zeros(M, (nq + 2 * nkv) * 128, device=dev, dtype=torch.bfloat16)
+            jobs[0] = ("qkv_store", [lw.qkv for lw in layers], G.EPI_STORE,
+                       lambda wt, c: ops.skinny_gemm(wt, x, ops.EPI_STORE, norm=True, out=qkv,
+                                                     waves=c))
         if not cfg.is_moe:
             F = layers[0].gate_up.shape[0] * 16 // 2
             act = torch.zeros(M, F, device=dev, dtype=torch.bfloat16)
@@ -180,7 +189,7 @@ def autotune_model(model, batch_sizes=(1,), verbose=False, table: dict | None = 
             times = {}
             fmt = G._fmt(wts[0])
             bf = fmt == "bf16"
-            norm = epi in (G.EPI_QKV_ROPE, G.EPI_SILU, G.EPI_ARGMAX)
+            norm = epi in (G.EPI_QKV_ROPE, G.EPI_SILU, G.EPI_ARGMAX) or name == "qkv_store"
             if fmt == "mx4":  # the MXFP4 kernel's own ladder (waves x U x NG), nothing else
                 codes = [c for c in G.MX4_CODES if G.mx4_code_ok(M, K, N, epi, norm, c)
                          and (K // 128) // (c & 0xff) >= 1]

@@ -64,9 +64,17 @@ class Engine:
                  seed: int = 0, kv_pages: int | None = None, max_prefill_tokens: int = 1024,
                  max_batch: int = 64, use_graph: bool = True, comm=None, tp_rank: int = 0,
                  tp_size: int = 1, kv_fraction: float = 0.85, ep_rank: int = 0,
-                 ep_size: int = 1, ep_mode: str = "allreduce", weight_dtype: str | None = None):
+                 ep_size: int = 1, ep_mode: str = "allreduce", weight_dtype: str | None = None,
+                 kv_dtype: str | None = None):
         self.cfg = cfg
         self.device = torch.device(device)
+        # kv_dtype "fp8": e4m3 KV pages with one fp32 scale per (token, kv head) row
+        # (engine.kv_cache, ops.kv_fp8): 0.516x the cache bytes per token, the unfused
+        # qkv -> quantising write -> FP8 attention route per layer (LlamaModel._forward_kv_fp8).
+        # Independent of weight_dtype; under TP/EP each rank quantises its own kv heads
+        self.kv_dtype = kv_dtype or os.environ.get("ENGINE_KV", "bf16")
+        if self.kv_dtype not in ("bf16", "fp8"):
+            raise ValueError("kv_dtype must be bf16 or fp8, got %r" % self.kv_dtype)
         own = weights is None
         # weight_dtype "fp8": weight-only e4m3 dense projections (EngineWeights.quantize_fp8);
         # "mxfp4": weight-only OCP MXFP4 projections and MoE experts + FP8 LM head
@@ -91,9 +99,9 @@ class Engine:
         self.weights = weights
         if kv_pages is None:
             self.kv = KVCache.from_free_memory(cfg, self.device, fraction=kv_fraction,
-                                               tp_size=tp_size)
+                                               tp_size=tp_size, kv_dtype=self.kv_dtype)
         else:
-            self.kv = KVCache(cfg, kv_pages, self.device, tp_size)
+            self.kv = KVCache(cfg, kv_pages, self.device, tp_size, kv_dtype=self.kv_dtype)
         if comm is not None and hasattr(comm, "setup"):
             comm.setup(self.device)
             if (cfg.is_moe and max(ep_size, weights.ep_size) > 1 and ep_mode == "a2a"
@@ -291,7 +299,8 @@ class Engine:
                     out_seq.append(b)
             greedy = all_logits is None and not sampled
             tiles_h = qtile = None
-            if self.flash_prefill_min and R >= self.flash_prefill_min:
+            # (FP8 pages have no flash kernel: the rows run the per-row FP8 attention)
+            if self.flash_prefill_min and R >= self.flash_prefill_min and self.kv_dtype == "bf16":
                 qtile = ops.flash_tile(self.model.nq, self.model.nkv, R)
                 tiles_h = ops.prefill_tiles(seq.tolist(), pos.tolist(), qtile)
             # every host-built input of the chunk (block tables, row metadata, output rows,

@@ -22,6 +22,9 @@ STRICT_SENDER, UI_FILE) and the engine knobs:
   ENGINE_WEIGHTS  bf16 (default) / fp8 (weight-only e4m3 projections) / mxfp4 (weight-only
                   OCP MXFP4 projections and MoE experts, 4.25 bits per weight, FP8 LM head;
                   ENGINE_TP=1 only)
+  ENGINE_KV       bf16 (default) / fp8 (e4m3 KV pages with one fp32 scale per token and kv
+                  head: 0.516x the cache bytes per token, so ~1.9x the tokens per GPU;
+                  independent of ENGINE_WEIGHTS, every TP/EP rank quantises its own kv heads)
   ENGINE_NATIVE_LOOP  1 (default) / 0: single-GPU replicas run the C++ step loop
                   (engine.native_loop) instead of the Python one
   ENGINE_TIMEOUT  per-request deadline in seconds (default 60, the reference UI's bound)
@@ -95,7 +98,7 @@ FLAGS = [
     ("--engine-max-tokens", "ENGINE_MAX_TOKENS"), ("--tokenizer", "TOKENIZER_PATH"),
     ("--engine-url", "ENGINE_URL"), ("--security", "SECURITY"), ("--nat-pmp", "NAT_PMP"), ("--upnp", "UPNP"),
     ("--engine-gpus", "ENGINE_GPUS"), ("--engine-tp", "ENGINE_TP"), ("--engine-ep", "ENGINE_EP"),
-    ("--engine-weights", "ENGINE_WEIGHTS"),
+    ("--engine-weights", "ENGINE_WEIGHTS"), ("--engine-kv", "ENGINE_KV"),
 ]
 
 

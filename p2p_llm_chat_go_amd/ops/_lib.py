@@ -83,6 +83,14 @@ _SIGS = {
     "p2p_pack_frag": [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p],
     "p2p_rope_cache": [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                        c_void_p, c_int, c_void_p, c_void_p, c_void_p],
+    # FP8 KV cache (kv_fp8_write.hip, kv_fp8_attention.hip): as p2p_rope_cache /
+    # p2p_paged_attention with (k codes, v codes, k scales, v scales) for the two pages
+    "p2p_rope_cache_fp8": [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                           c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                           c_void_p],
+    "p2p_paged_attention_fp8": [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float,
+                                c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p],
     "p2p_argmax": [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p],
     "p2p_advance": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
                     c_int, c_void_p, c_int, c_void_p],
