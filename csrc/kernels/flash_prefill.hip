@@ -16,17 +16,13 @@
 // O(T^2): here each K/V tile is read once per 16 query tokens x G heads.
 // Behavioural parity: the reference delegates prompt processing to an external
 // Ollama server (`web/streamlit_app.py:89-101`), see SURVEY.md §2B.2 B2.3.
-#include "common.h"
+#include "flash_tile.h"  // PAGE, HD, Tile; v2: the page images and kperm
 
 namespace {
 
-constexpr int PAGE = 64, HD = 128, KT = 32, QT = 16;
+constexpr int KT = 32, QT = 16;
 constexpr int KLD = HD + 8;   // K tile row stride (bf16), breaks LDS bank aliasing
 constexpr int VLD = KT + 4;   // V^T tile row stride (bf16), 8-byte aligned rows
-
-struct Tile {
-  int row0, n, seq, pos0;
-};
 
 template <int G>
 __global__ __launch_bounds__(64 * G) void flash_prefill_kernel(
@@ -212,16 +208,7 @@ int launch(const bf16* q, int ldq, const bf16* kc, const bf16* vc, const int* bt
 // conflict-free b128 reads), V transposed to [d][key] (144-B rows) while staging.
 // The next page's global loads are issued right after the barrier and land in
 // registers while the MFMAs run (one barrier per tile, two LDS stages).
-constexpr int KLD2 = HD + 8;  // K image row stride (bf16)
-constexpr int VLD2 = 64 + 8;  // V^T image row stride (bf16)
-constexpr int KS_ELEMS = 64 * KLD2, VS_ELEMS = HD * VLD2;
-
-typedef float f32x16_t __attribute__((ext_vector_type(16)));
-
-__device__ __forceinline__ int kperm(int rho) {  // S^T row rho -> key within the 32-key half
-  const int s = rho >> 4, r = rho & 15;
-  return 16 * s + 8 * ((r >> 2) & 1) + 4 * (r >> 3) + (r & 3);
-}
+// (KLD2 / VLD2, the strides of the two images, and kperm: flash_tile.h)
 
 template <int G>
 __global__ __launch_bounds__(512) void flash_prefill2_kernel(

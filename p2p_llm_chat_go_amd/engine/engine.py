@@ -299,9 +299,9 @@ class Engine:
                     out_seq.append(b)
             greedy = all_logits is None and not sampled
             tiles_h = qtile = None
-            # (FP8 pages have no flash kernel: the rows run the per-row FP8 attention)
-            if self.flash_prefill_min and R >= self.flash_prefill_min and self.kv_dtype == "bf16":
-                qtile = ops.flash_tile(self.model.nq, self.model.nkv, R)
+            # (FP8 pages: a 16-token width means the rows run the per-row FP8 attention)
+            if self.flash_prefill_min and R >= self.flash_prefill_min:
+                qtile = ops.flash_tile(self.model.nq, self.model.nkv, R, kv_dtype=self.kv_dtype)
                 tiles_h = ops.prefill_tiles(seq.tolist(), pos.tolist(), qtile)
             # every host-built input of the chunk (block tables, row metadata, output rows,
             # flash tiles, result scatter) in ONE host->device copy: each separate copy of

@@ -285,7 +285,9 @@ class PrefillGraph:
         self.rows, self.n_seq, self.max_pages, self.max_ctx = rows, n_seq, max_pages, max_ctx
         self.n_out = n_seq
         self.greedy = greedy
-        self.qtile = ops.flash_tile(model.nq, model.nkv, rows)
+        # (a model without a cache, as the host-side layout is built for, cuts bf16 tiles)
+        kv_dtype = getattr(getattr(model, "kv", None), "kv_dtype", "bf16")
+        self.qtile = ops.flash_tile(model.nq, model.nkv, rows, kv_dtype=kv_dtype)
         # tiles never straddle sequences: <= rows / qtile + one partial tile per sequence
         # (the dummy sequence included) + one per wrap of the dummy rows' positions
         self.max_tiles = -(-rows // self.qtile) + n_seq + 1 + rows // (max_pages * PAGE) + 1

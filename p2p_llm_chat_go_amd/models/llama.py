@@ -207,7 +207,8 @@ class LlamaModel:
         ops.gather_rows(self.w.embed, ids[:R], out=h)
         if self.kv.kv_dtype == "fp8":
             return self._forward_kv_fp8(ws, h, pos, slots, block_tables, row_bt, ctx_lens, R,
-                                        max_ctx, out_rows, n_out, greedy)
+                                        max_ctx, out_rows, n_out, greedy, tiles, tiles_host,
+                                        qtile)
         if (self.decode_engine and tiles is None and row_bt is None and out_rows is None
                 and self._decode_engine_ok(R, max_ctx)):
             self._de.run(h, pos[:R], slots[:R], self.rope, block_tables, ctx_lens[:R], ws.err)
@@ -264,28 +265,36 @@ class LlamaModel:
         return self._head(ws, h, R, out_rows, n_out, greedy)
 
     def _forward_kv_fp8(self, ws: Workspace, h, pos, slots, block_tables, row_bt, ctx_lens,
-                        R: int, max_ctx: int, out_rows, n_out, greedy: bool):
+                        R: int, max_ctx: int, out_rows, n_out, greedy: bool, tiles=None,
+                        tiles_host=None, qtile=None):
         """The layers over an FP8 KV cache (``KVCache(kv_dtype="fp8")``), per layer:
 
             qkv   = rstd(h) * h @ Wqkv'          skinny_gemm  NORM | STORE (permuted columns)
             q     = rope(qkv), K/V -> e4m3 pages   ops.rope_cache_fp8 (quantising write)
-            a     = attention(q, e4m3 pages)       ops.paged_attention_fp8
+            a     = attention(q, e4m3 pages)       ops.paged_attention_fp8 / flash_prefill_fp8
             h    += a @ Wo;  MLP                   as the bf16 route
 
         Every kernel that writes or reads bf16 pages is off here: the QKV_ROPE epilogues,
-        ``qkv_attn``, ``attn_oproj*``, the persistent decode engine and flash prefill.
-        Prompt chunks run the same attention kernel with one query row per token
-        (``row_bt`` + ``ctx = pos + 1``), so the flash tiles are not used."""
+        ``qkv_attn``, ``attn_oproj*``, the persistent decode engine and the bf16 flash prefill.
+        Prompt chunks whose tiles were cut wider than 16 tokens (``ops.flash_tile`` with
+        ``kv_dtype="fp8"``) run the FP8 flash prefill; the others run the per-row attention
+        kernel with one query row per token (``row_bt`` + ``ctx = pos + 1``)."""
         cfg = self.cfg
         qkv, q, attn = ws.qkv[:R], ws.q[:R], ws.attn[:R]
         rb = row_bt[:R] if row_bt is not None else None
+        flash = tiles is not None and qtile is not None and qtile > ops.attention.QTILE
         for i, lw in enumerate(self.w.layers):
             kc, vc, ks, vs = self.kv.layer_fp8(i)
             ops.skinny_gemm(lw.qkv, h, ops.EPI_STORE, norm=True, out=qkv, eps=cfg.eps)
             ops.rope_cache_fp8(qkv, pos[:R], slots[:R], self.rope, self.nq, self.nkv, q, kc, vc,
                                ks, vs)
-            ops.paged_attention_fp8(q, kc, vc, ks, vs, block_tables, rb, ctx_lens[:R], self.nq,
-                                    self.nkv, max_ctx, out=attn, workspace=ws.attn_ws)
+            if flash:
+                ops.flash_prefill_fp8(q, kc, vc, ks, vs, block_tables, tiles, self.nq, self.nkv,
+                                      out=attn, tiles_host=tiles_host, qtile=qtile)
+            else:
+                ops.paged_attention_fp8(q, kc, vc, ks, vs, block_tables, rb, ctx_lens[:R],
+                                        self.nq, self.nkv, max_ctx, out=attn,
+                                        workspace=ws.attn_ws)
             self._row_parallel(lw.o, attn, h, ws, R)
             self._mlp(lw, ws, R)
         return self._head(ws, h, R, out_rows, n_out, greedy)

@@ -15,7 +15,8 @@ from .attention import (PAGE, HEAD_DIM, attn_oproj, attn_oproj_ok, attn_oproj_he
                         attn_oproj_heads_ok, attn_oproj_heads_workspace, attn_workspace,
                         flash_prefill, flash_tile, paged_attention, prefill_tiles, rope_cache,
                         qkv_attn, qkv_attn_ok, qkv_attn_oproj_ok, qkv_attn_workspace)
-from .kv_fp8 import (dequantize_kv, paged_attention_fp8, quantize_kv_rows, rope_cache_fp8)
+from .kv_fp8 import (dequantize_kv, flash_prefill_fp8, paged_attention_fp8, quantize_kv_rows,
+                     rope_cache_fp8)
 from .moe import mx4_grouped_ok, mx4_grouped_prefill_ok, mx4_grouped_route
 from .elementwise import advance, argmax, gather_rows, l3_prefetch
 from .sampling import sample, sample_candidates, topk_candidates
@@ -32,5 +33,6 @@ __all__ = [
     "attn_oproj_heads_workspace", "tiled_split_fault", "tiled_split_parallel", "l3_prefetch",
     "rope_cache", "qkv_attn", "qkv_attn_ok", "qkv_attn_oproj_ok", "qkv_attn_workspace", "sample", "sample_candidates", "topk_candidates", "advance", "argmax", "gather_rows", "kernels_available", "kernel_lib",
     "kernel_lib_path",
-    "rope_cache_fp8", "paged_attention_fp8", "quantize_kv_rows", "dequantize_kv",
+    "rope_cache_fp8", "paged_attention_fp8", "flash_prefill_fp8", "quantize_kv_rows",
+    "dequantize_kv",
 ]

@@ -91,6 +91,10 @@ _SIGS = {
     "p2p_paged_attention_fp8": [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                 c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float,
                                 c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p],
+    # kv_fp8_flash_prefill.hip: as p2p_flash_prefill2 over the code pages and scale planes
+    "p2p_flash_prefill_fp8": [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                              c_int, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p,
+                              c_int, c_void_p],
     "p2p_argmax": [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p],
     "p2p_advance": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
                     c_int, c_void_p, c_int, c_void_p],

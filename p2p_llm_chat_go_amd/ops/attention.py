@@ -283,10 +283,28 @@ FLASH_V2 = os.environ.get("P2P_FLASH_V2", "1") != "0"
 FLASH_V2_MIN_BLOCKS = 128  # v1 wins up to T=512 at 8 KV heads, v2 from ~1K (profiles/r2_flash_prefill_v2_conflict_free.jsonl)
 
 
-def flash_tile(n_heads: int, n_kv: int, rows: int | None = None) -> int:
+# FP8 pages: the flash prefill (kv_fp8_flash_prefill.hip) against the per-row kernel on the
+# same rows, from this many (query tile, kv head) workgroups.  32 is the smallest count
+# measured at both head shapes, and the flash kernel wins there and everywhere above by far
+# more than the spread (profiles/kv_fp8_flash.jsonl, us flash / per-row, spread <= 0.6 %):
+# 8B heads 256 rows = 32 workgroups 17.6 / 31.4; 70B heads 128 rows = 32 workgroups
+# 12.7 / 35.0; 512 rows 27.1 / 135.0 and 27.3 / 243.0; 2048 rows 83.3 / 1617 and 96.2 / 3032.
+# (8B heads 128 rows = 16 workgroups: 12.2 / 14.8, not measured at the 70B shape.)
+FLASH_FP8_MIN_BLOCKS = 32
+
+
+def flash_tile(n_heads: int, n_kv: int, rows: int | None = None, kv_dtype: str = "bf16") -> int:
     """Tokens per query tile for a prefill chunk of ``rows`` tokens: v2 (256 / (Hq/Hkv))
-    when it yields enough workgroups, else v1 (16)."""
+    when it yields enough workgroups, else v1 (16).  ``kv_dtype="fp8"``: 256 / (Hq/Hkv) for
+    ``ops.flash_prefill_fp8`` from FLASH_FP8_MIN_BLOCKS workgroups, else 16 -- which on an FP8
+    cache means the per-row kernel (``ops.paged_attention_fp8``): it has no 16-token kernel."""
     G = n_heads // n_kv
+    if kv_dtype == "fp8":
+        if G in (1, 2, 4, 8) and n_heads == G * n_kv:
+            t = 256 // G
+            if rows is None or -(-rows // t) * n_kv >= FLASH_FP8_MIN_BLOCKS:
+                return t
+        return QTILE
     if FLASH_V2 and G in (1, 2, 4, 8):
         t = 256 // G
         if rows is None or -(-rows // t) * n_kv >= FLASH_V2_MIN_BLOCKS:

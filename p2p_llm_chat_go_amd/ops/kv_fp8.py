@@ -7,8 +7,8 @@ Cache format (per layer, for K and for V; ``engine/kv_cache.py`` with ``kv_dtype
 
 For a row x (K after RoPE, V as projected): ``s = amax(|x|) / 448`` (1 for a zero row),
 ``code = e4m3_rne(x / s)``, ``dequant = float(code) * s``.  GPU tensors run
-``csrc/kernels/kv_fp8_write.hip`` / ``kv_fp8_attention.hip``; CPU tensors the PyTorch
-reference of the same rule.
+``csrc/kernels/kv_fp8_write.hip`` / ``kv_fp8_attention.hip`` / ``kv_fp8_flash_prefill.hip``
+(prompt chunks, ``flash_prefill_fp8``); CPU tensors the PyTorch reference of the same rule.
 """
 from __future__ import annotations
 
@@ -140,4 +140,47 @@ def paged_attention_fp8(q: torch.Tensor, k_codes: torch.Tensor, v_codes: torch.T
         ctx_lens.data_ptr(), R, n_heads, n_kv, HEAD_DIM, float(scale), int(max_ctx),
         out.data_ptr(), out.stride(0), _lib.ptr(po), _lib.ptr(pml), _lib.stream_ptr(q.device)),
         "paged_attention_fp8")
+    return out
+
+
+def flash_prefill_fp8(q: torch.Tensor, k_codes: torch.Tensor, v_codes: torch.Tensor,
+                      k_scale: torch.Tensor, v_scale: torch.Tensor, block_tables: torch.Tensor,
+                      tiles: torch.Tensor, n_heads: int, n_kv: int,
+                      out: torch.Tensor | None = None, scale: float | None = None,
+                      tiles_host: torch.Tensor | None = None, *, qtile: int) -> torch.Tensor:
+    """``ops.flash_prefill`` over FP8 pages (``csrc/kernels/kv_fp8_flash_prefill.hip``): causal
+    MFMA attention for query tiles cut by ``prefill_tiles(seq, pos, qtile)`` with
+    ``qtile = flash_tile(n_heads, n_kv, rows, kv_dtype="fp8")`` = 256 / (n_heads / n_kv); there
+    is no 16-token FP8 kernel.  Same result as :func:`paged_attention_fp8` with one row per
+    prompt token (ctx = pos + 1), reading each page once per tile instead of once per row."""
+    if qtile is None or qtile < 1:
+        raise ValueError("flash_prefill_fp8: qtile (the prefill_tiles width) is required")
+    if tiles_host is not None and tiles_host.numel() and int(tiles_host[:, 1].max()) > qtile:
+        raise ValueError("flash_prefill_fp8: tiles are wider than qtile=%d" % qtile)
+    R = q.shape[0]
+    if scale is None:
+        scale = 1.0 / math.sqrt(HEAD_DIM)
+    if out is None:
+        out = torch.empty(R, n_heads * HEAD_DIM, device=q.device, dtype=q.dtype)
+    assert k_codes.dtype == F8 and v_codes.dtype == F8 and k_scale.dtype == torch.float32
+    if q.device.type != "cuda":
+        th = (tiles_host if tiles_host is not None else tiles).cpu()
+        row_bt = torch.empty(R, dtype=torch.int32)
+        ctx = torch.empty(R, dtype=torch.int32)
+        for r0, n, s, p0 in th.tolist():
+            row_bt[r0:r0 + n] = s
+            ctx[r0:r0 + n] = torch.arange(p0 + 1, p0 + n + 1, dtype=torch.int32)
+        return paged_attention_fp8_ref(q, k_codes, v_codes, k_scale, v_scale, block_tables,
+                                       row_bt, ctx, n_heads, n_kv, scale, out)
+    G = n_heads // n_kv
+    if n_heads % n_kv or G not in (1, 2, 4, 8) or qtile * G != 256:
+        raise ValueError("flash_prefill_fp8: needs n_heads / n_kv in (1, 2, 4, 8) and tiles of "
+                         "256 / (n_heads / n_kv) tokens, got %d / %d heads, qtile=%d"
+                         % (n_heads, n_kv, qtile))
+    assert q.stride(1) == 1 and out.stride(1) == 1
+    _lib.check(_lib.lib().p2p_flash_prefill_fp8(
+        q.data_ptr(), q.stride(0), k_codes.data_ptr(), v_codes.data_ptr(), k_scale.data_ptr(),
+        v_scale.data_ptr(), block_tables.data_ptr(), block_tables.stride(0), tiles.data_ptr(),
+        tiles.shape[0], n_heads, n_kv, HEAD_DIM, float(scale), out.data_ptr(), out.stride(0),
+        _lib.stream_ptr(q.device)), "flash_prefill_fp8")
     return out
