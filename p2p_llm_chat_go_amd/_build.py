@@ -97,8 +97,8 @@ EXPERIMENTAL_LIB = os.path.join(LIBDIR, "libp2p_experimental.so")
 # it before it lands.  Their translation units must compile with zero scratch.
 NO_SCRATCH = {"wide_gemm.hip", "tiled_gemm.hip", "mx4_gemm.hip", "mx4_prefill_gemm.hip",
               "mx4_moe_gemm.hip", "mx4_moe_prefill_gemm.hip", "kv_fp8_write.hip",
-              "kv_fp8_attention.hip", "kv_fp8_flash_prefill.hip"}
-# (the mx4_* units: plain loads, but their launch ladders promise
+              "kv_fp8_attention.hip", "kv_fp8_flash_prefill.hip", "fp8_prefill_gemm.hip"}
+# (the mx4_* units and fp8_prefill_gemm.hip: plain loads, but their launch ladders promise
 # instantiations that fit the register file -- a spilling one means the ladder is off;
 # kv_fp8_attention.hip: its G <= 4 instantiations are held at 64 VGPRs for two blocks per CU;
 # kv_fp8_flash_prefill.hip: ~207 of the 256 VGPRs a 512-thread block may hold)

@@ -9,6 +9,7 @@ from .gemm import (EPI_AR, EPI_F32, EPI_RESID, EPI_SILU, EPI_STORE, Fp8Weight, s
                    skinny_gemm_ar, argmax_finalize, fold_norm,
                    quantize_fp8, Mx4Weight, quantize_mxfp4, MX4_CODES, mx4_code_ok,
                    MX4_PREFILL_CODES, MX4_PREFILL_FLAG, mx4_prefill_ok, mx4_route,
+                   FP8_PREFILL_CODES, FP8_PREFILL_FLAG, fp8_prefill_ok, fp8_route,
                    lm_head_argmax, new_argmax_keys, qkv_rope_gemm, rope_row_perm, skinny_gemm, tile_weight,
                    tiled_shape, tiled_split_fault, tiled_split_parallel, untile_weight)
 from .attention import (PAGE, HEAD_DIM, attn_oproj, attn_oproj_ok, attn_oproj_heads,
@@ -25,6 +26,7 @@ from ._lib import available as kernels_available, lib as kernel_lib, lib_path as
 __all__ = [
     "Mx4Weight", "quantize_mxfp4", "MX4_CODES", "mx4_code_ok",
     "MX4_PREFILL_CODES", "MX4_PREFILL_FLAG", "mx4_prefill_ok", "mx4_route",
+    "FP8_PREFILL_CODES", "FP8_PREFILL_FLAG", "fp8_prefill_ok", "fp8_route",
     "mx4_grouped_ok", "mx4_grouped_prefill_ok", "mx4_grouped_route",
     "EPI_AR", "skinny_ar_ok", "skinny_gemm_ar", "EPI_F32", "EPI_RESID", "EPI_SILU", "EPI_STORE", "fold_norm", "skinny_gemm", "tile_weight",
     "tiled_shape", "untile_weight", "argmax_finalize", "lm_head_argmax", "new_argmax_keys", "qkv_rope_gemm",

@@ -118,6 +118,13 @@ _SIGS = {
                                       c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                       c_void_p, c_void_p, c_float, c_int, c_void_p],
     "p2p_mx4_prefill_ok": [c_int, c_int, c_int, c_int, c_int, c_int],
+    # FP8 prefill GEMM (fp8_prefill_gemm.hip, M > 64): codes, per-channel scales, then the same
+    "p2p_fp8_prefill_gemm": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                             c_int, c_void_p, c_int, c_float, c_int, c_void_p],
+    "p2p_fp8_prefill_gemm_qkv_rope": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                                      c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                      c_void_p, c_void_p, c_float, c_int, c_void_p],
+    "p2p_fp8_prefill_ok": [c_int, c_int, c_int, c_int, c_int, c_int],
     "p2p_sample": [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                    c_void_p, c_void_p],
     "p2p_topk_candidates": [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p],

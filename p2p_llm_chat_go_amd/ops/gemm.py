@@ -266,6 +266,43 @@ def mx4_route(M: int, K: int, N: int, epi: int, norm: bool) -> str:
 _MX4_PREFILL_96 = {(4096, 4096), (28672, 4096), (10240, 8192), (57344, 8192)}
 
 
+# launch-code bit: the FP8 prefill kernel (csrc/kernels/fp8_prefill_gemm.hip: one 8-wave
+# workgroup per BM x BN tile over the whole K, M > 64, Fp8Weight planes as they are); below
+# it the fields of MX4_PREFILL_FLAG: bits 0..3 = BM / 64, bits 4..7 = BN / 64.  The flag alone
+# means the default tile.  It never reaches p2p_skinny_gemm* (_fp8_prefill)
+FP8_PREFILL_FLAG = 1 << 30
+FP8_PREFILL_CODES = [FP8_PREFILL_FLAG | (bm // 64) | ((bn // 64) << 4)
+                     for bm in (64, 128, 256, 512) for bn in (64, 128)]  # 512 rows: not served
+
+
+def fp8_prefill_ok(M: int, K: int, N: int, epi: int, norm: bool, code: int = 0) -> bool:
+    """Does the FP8 prefill kernel serve this shape with this tile code (0 = its default)?"""
+    if code and not code & FP8_PREFILL_FLAG:
+        return False
+    return bool(_lib.lib().p2p_fp8_prefill_ok(M, K, N, int(epi), int(bool(norm)), int(code) & 0xff))
+
+
+def fp8_route(M: int, K: int, N: int, epi: int, norm: bool) -> str:
+    """Which kernel an FP8 projection of M rows runs on with no explicit launch code:
+    "prefill" (fp8_prefill_gemm.hip, one launch) or "skinny" (the skinny kernel's F8 path, one
+    launch per 64 rows).  Pure: the shape rules of the prefill kernel and the measured
+    thresholds."""
+    if M <= SKINNY_MAX_M or K % 128 or N % (32 if epi == EPI_SILU else 16):
+        return "skinny"
+    if epi not in (EPI_STORE, EPI_RESID, EPI_SILU, EPI_F32, EPI_QKV_ROPE):
+        return "skinny"
+    if epi == EPI_QKV_ROPE and not norm:
+        return "skinny"
+    # profiles/fp8_prefill_gemm.jsonl (bench/fp8_prefill_bench.py; llama3.1-8B and -70B
+    # projections, 96..1024 rows, cold weights; the two passes of one record differed by 11.8 %
+    # at most, 1.2 % in the median).  The prefill kernel's best tile beat the 64-row chunks at
+    # every shape and row count by more than the record's spread: 1.10x (8B down, 96 rows,
+    # spread 0.7 %) and 1.31x (8B o, 96 rows) at the low end, 2.0x .. 2.5x for the other
+    # shapes at 96 rows, 3.1x (70B gate_up) .. 8.7x (8B qkv) at 1024 rows.  So no bucket keeps
+    # the chunks.  65..95 rows: not measured (the engine's row buckets go from 64 to 96).
+    return "prefill"
+
+
 def m_tile(M: int) -> int:
     """Autotune bucket of M: 16-row MFMA tiles (1..4).  The skinny kernel runs 3 tiles as
     4; the midm / tiled kernels use the exact count, so 33-48 rows tune separately."""
@@ -383,7 +420,7 @@ def pack_frag(x: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
 
 
 def _want_tiled(wt, M, N, K, epi, norm, waves) -> bool:
-    if _fmt(wt) != "bf16":  # FP8: the skinny kernel in M chunks of 64; MXFP4: _mx4_prefill
+    if _fmt(wt) != "bf16":  # FP8: _fp8_prefill; MXFP4: _mx4_prefill
         return False
     if use_tiled(M, N, K, epi):
         return True
@@ -399,6 +436,14 @@ def _mx4_prefill(M, K, N, epi, norm, waves) -> bool:
     if waves:
         return bool(waves & MX4_PREFILL_FLAG)
     return mx4_route(M, K, N, epi, norm) == "prefill"
+
+
+def _fp8_prefill(M, K, N, epi, norm, waves) -> bool:
+    """As _mx4_prefill for an FP8 projection: an explicit prefill code (one its ladder does not
+    serve then fails the launch) or, with no code, fp8_route; a skinny code keeps the chunks."""
+    if waves:
+        return bool(waves & FP8_PREFILL_FLAG)
+    return fp8_route(M, K, N, epi, norm) == "prefill"
 
 
 def tiled_config(version: int = 2, tile: int = 0, splitk: int = 0):
@@ -495,7 +540,7 @@ def skinny_gemm(wt: torch.Tensor, x: torch.Tensor, epi: int = EPI_STORE, norm: b
                 out: torch.Tensor | None = None, eps: float = 1e-5, waves: int = 0,
                 x_packed: bool = False) -> torch.Tensor:
     """out = epi(rstd(x) * x @ W^T) for x [M, K] with M <= 64 (rows > 64 are chunked, or run
-    the tiled / MXFP4 prefill kernel where the weight format has one: _want_tiled, mx4_route).
+    the tiled / MXFP4 / FP8 prefill kernel of the weight format: _want_tiled, mx4_route, fp8_route).
     A launch code with AFRAG_FLAG packs x fragment-major first (pack_frag) unless
     ``x_packed`` says the caller already did (then x is pack_frag's output, rows <= 64)."""
     N, K = tiled_shape(wt)
@@ -528,6 +573,12 @@ def skinny_gemm(wt: torch.Tensor, x: torch.Tensor, epi: int = EPI_STORE, norm: b
         _lib.check(L.p2p_mx4_prefill_gemm(wp, sp, x.data_ptr(), x.stride(0), M, K, N, epi,
                                           int(norm), out.data_ptr(), out.stride(0), float(eps),
                                           waves & 0xff, s), "mx4_prefill_gemm")
+        return out
+    if _fmt(wt) == "fp8" and _fp8_prefill(M, K, N, epi, norm, waves):
+        wp, sp = _wptr(wt)
+        _lib.check(L.p2p_fp8_prefill_gemm(wp, sp, x.data_ptr(), x.stride(0), M, K, N, epi,
+                                          int(norm), out.data_ptr(), out.stride(0), float(eps),
+                                          waves & 0xff, s), "fp8_prefill_gemm")
         return out
     for m0 in range(0, M, SKINNY_MAX_M):
         mc = min(SKINNY_MAX_M, M - m0)
@@ -632,6 +683,14 @@ def qkv_rope_gemm(wt, x, pos, slots, cos_sin, n_heads, n_kv, q_out, k_cache, v_c
             slots.data_ptr(), cos_sin.data_ptr(), q_out.data_ptr(), q_out.stride(0),
             k_cache.data_ptr(), v_cache.data_ptr(), float(eps), waves & 0xff, s),
             "mx4_prefill_gemm_qkv_rope")
+        return q_out
+    if _fmt(wt) == "fp8" and _fp8_prefill(M, K, N, EPI_QKV_ROPE, True, waves):
+        wp, sp = _wptr(wt)
+        _lib.check(L.p2p_fp8_prefill_gemm_qkv_rope(
+            wp, sp, x.data_ptr(), x.stride(0), M, K, n_heads, n_kv, pos.data_ptr(),
+            slots.data_ptr(), cos_sin.data_ptr(), q_out.data_ptr(), q_out.stride(0),
+            k_cache.data_ptr(), v_cache.data_ptr(), float(eps), waves & 0xff, s),
+            "fp8_prefill_gemm_qkv_rope")
         return q_out
     for m0 in range(0, M, SKINNY_MAX_M):
         mc = min(SKINNY_MAX_M, M - m0)
